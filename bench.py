@@ -15,6 +15,11 @@ BERT configuration (BASELINE.json "FewRel 10-way 5-shot with BERT-base encoder")
   python bench.py --encoder bert   (10-way 5-shot Q=5, BERT-base 12x768, L=128, 8 episodes/GPU)
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes-per-gpu B] [--shot K]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what takes work
+of its own after the timed region: ``phase_ms`` (per-phase HIP-event times from a few extra profiled steps)
+and ``params_in_sync`` (the cross-rank parameter comparison).  ``--dump-outputs DIR`` writes what the last
+timed step returned and left behind (``dump_outputs`` below) as ``DIR/<name>.npy``.
 Multi-GPU, either form:
   python bench.py --gpus N       (no launcher: this process starts N rank processes itself -- before it
                                   touches the GPU -- and exits non-zero if any rank fails or times out)
@@ -88,6 +93,26 @@ def launch_ranks(n: int, argv, timeout_s: float) -> int:
     return rc
 
 
+DUMP_CAP_BYTES = 16 << 20   # per array; at most four arrays are written, 64 MB in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each tensor / number of ``arrays`` as ``out_dir/<name>.npy`` (float32; float64 stays float64).
+    An array above DUMP_CAP_BYTES is reduced to a fixed sample: the elements at seeded (seed 0), sorted,
+    distinct flat indices, the same ones for every run of the same shape."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = DUMP_CAP_BYTES // (8 if dt == torch.float64 else 4)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -120,6 +145,13 @@ def main():
                     help="cpu: the oracle path (launcher / plumbing tests only; not a benchmark)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="self-launched multi-rank run: kill every rank after this many seconds")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: train: "
+                         "loss, accuracy, params (the flat trainable parameters it updated) and grad (the flat "
+                         "gradient it applied); eval: accuracy.  Rank 0 writes; float32, a seeded sample above 16 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also report phase_ms (extra profiled steps after the timed region) and params_in_sync "
+                         "(cross-rank parameter comparison); a plain run only times the steps")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
@@ -176,9 +208,9 @@ def main():
     dist.barrier()
     sync()
     t0 = time.perf_counter()
-    loss_t = None
+    loss_t = acc_t = None
     for _ in range(args.steps):
-        loss_t, _ = step()
+        loss_t, acc_t = step()
     sync()
     dist.barrier()
     sync()
@@ -186,11 +218,14 @@ def main():
     rank_ms = [round(1000 * float(x) / args.steps, 3) for x in dist.all_gather_objects(dt_rank)]
     dt = dist.max_scalar(dt_rank)
     loss = float(loss_t) if loss_t is not None else float("nan")
+    if args.dump_outputs and dist.is_main and loss_t is not None:   # before any further step touches the state
+        dump_outputs(args.dump_outputs, {"accuracy": loss_t} if evalm else
+                     {"loss": loss_t, "accuracy": acc_t, "params": tr.flat.flat, "grad": tr.flat.grad})
     # per-phase GPU time (HIP events at the phase boundaries of the eager train step: device sampling,
     # forward + backward (incl. the head-span all-reduce overlapped with it), the EXPOSED all-reduce tail,
-    # optimizer), from a few extra steps AFTER the timed region; MAX over ranks per phase
+    # optimizer), from a few extra steps AFTER the timed region; MAX over ranks per phase (--full only)
     phase_ms = None
-    if cuda and not evalm and not tr.graph_step_enabled:
+    if args.full and cuda and not evalm and not tr.graph_step_enabled:
         tr.cfg = tr.cfg.replace(profile=True)
         n_prof = max(1, min(5, args.steps))
         for _ in range(n_prof):
@@ -198,7 +233,7 @@ def main():
         sync()
         ph = tr.drain_phase_events()
         phase_ms = {k: round(dist.max_scalar(v / n_prof), 3) for k, v in ph.items()}
-    in_sync = dist.params_in_sync(tr.flat.flat)
+    in_sync = dist.params_in_sync(tr.flat.flat) if args.full else None
     episodes = args.steps * B * world
     value = episodes / dt
     if dist.is_main:
@@ -232,7 +267,7 @@ def main():
                          "full-L parity" + (", ragged tiles" if args.ragged else "")),
             },
             ("eval_accuracy" if evalm else "final_loss"): round(loss, 6),
-            "params_in_sync": bool(in_sync),
+            "params_in_sync": bool(in_sync) if args.full else None,
             "rccl_world": (torch.distributed.get_world_size() if dist.initialized else 1),
             "backend": dist.backend or "none",
             "comm": dist.comm_name,

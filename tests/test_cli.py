@@ -4,10 +4,9 @@ import os
 import subprocess
 import sys
 
-import pytest
+from golden_data import fewrel_val_json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VAL = "/root/reference/data/val.json"
 
 
 def _run(args, cwd):
@@ -30,8 +29,8 @@ def test_positional_cli_synthetic(tmp_path):
     assert {r["kind"] for r in recs} >= {"train", "val", "test"}
 
 
-@pytest.mark.skipif(not os.path.exists(VAL), reason="reference val.json not mounted")
 def test_real_val_json_relation_split(tmp_path):
+    VAL = fewrel_val_json(tmp_path)
     r = _run(["induction", "5", "2", "--val_file", VAL, "--split_val", "true", "--vocab_from_data", "true",
               "--processed_dir", str(tmp_path / "_processed_data"), "--train_iter", "2", "--val_step", "2",
               "--val_iter", "2", "--test_iter", "2", "--device", "cpu", "--model_dir", str(tmp_path / "ck")], tmp_path)
@@ -39,9 +38,9 @@ def test_real_val_json_relation_split(tmp_path):
     assert "Test accuracy:" in r.stdout
 
 
-@pytest.mark.skipif(not os.path.exists(VAL), reason="reference val.json not mounted")
 def test_val_relations_must_not_reach_the_test_block(tmp_path):
     """--fold with --val_relations: the validation block may not wrap into the held-out test relations."""
+    VAL = fewrel_val_json(tmp_path)
     r = _run(["induction", "5", "1", "--val_file", VAL, "--split_val", "true", "--vocab_from_data", "true",
               "--processed_dir", str(tmp_path / "_processed_data"), "--fold", "0", "--val_relations", "9",
               "--train_iter", "2", "--device", "cpu", "--model_dir", str(tmp_path / "ck")], tmp_path)

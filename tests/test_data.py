@@ -1,19 +1,22 @@
-"""Data-format contracts on the only real data in-tree: reference/data/val.json."""
+"""Data-format contracts on the only real data in-tree: the FewRel val.json (tests/golden)."""
 import json
-import os
 
 import numpy as np
 import pytest
 
+from golden_data import fewrel_val_json
+
 from induction_network_on_fewrel_amd.data import (EpisodeSampler, FewRelDataset, make_synthetic,
                                                   truncate_word_vectors, vocab_from_fewrel)
 
-VAL = "/root/reference/data/val.json"
-needs_val = pytest.mark.skipif(not os.path.exists(VAL), reason="reference val.json not mounted")
+@pytest.fixture(scope="module")
+def val_json(tmp_path_factory):
+    return fewrel_val_json(tmp_path_factory.mktemp("golden"))
 
 
 @pytest.fixture(scope="module")
-def val_ds(tmp_path_factory):
+def val_ds(tmp_path_factory, val_json):
+    VAL = val_json
     d = tmp_path_factory.mktemp("fewrel")
     wv = d / "wv.json"
     with open(wv, "w") as fh:
@@ -22,7 +25,6 @@ def val_ds(tmp_path_factory):
                                    verbose=False), d, wv
 
 
-@needs_val
 def test_val_shapes_and_ranges(val_ds):
     ds, _, _ = val_ds
     assert ds.num_relations == 16 and ds.num_instances == 11200
@@ -36,11 +38,10 @@ def test_val_shapes_and_ranges(val_ds):
     assert 0.30 < pad < 0.36
 
 
-@needs_val
-def test_tensorization_matches_reference_loop(val_ds):
+def test_tensorization_matches_reference_loop(val_ds, val_json):
     """Re-derive a few rows with the reference's literal per-token loop (data_loader.py:155-192)."""
     ds, _, _ = val_ds
-    with open(VAL) as fh:
+    with open(val_json) as fh:
         ori = json.load(fh)
     L = 37
     w2i = ds.word2id
@@ -68,9 +69,9 @@ def test_tensorization_matches_reference_loop(val_ds):
         i += 1
 
 
-@needs_val
-def test_cache_roundtrip(val_ds):
+def test_cache_roundtrip(val_ds, val_json):
     ds, d, wv = val_ds
+    VAL = val_json
     again = FewRelDataset.from_json(VAL, str(wv), max_length=37, processed_dir=str(d / "_processed_data"),
                                     verbose=False)
     assert (again.data_word == ds.data_word).all() and again.rel2scope == ds.rel2scope

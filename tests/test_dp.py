@@ -139,7 +139,7 @@ def test_bench_self_launch_cpu(world):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "INA_FAULT_STEP"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--device", "cpu", "--steps", "2",
-           "--warmup", "1", "--episodes-per-gpu", "2", "--launch-timeout", "240"]
+           "--warmup", "1", "--episodes-per-gpu", "2", "--launch-timeout", "240", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -151,3 +151,39 @@ def test_bench_self_launch_cpu(world):
     bad = subprocess.run(cmd, cwd=root, env=dict(env, INA_FAULT_STEP="1", INA_FAULT_RANK=str(world - 1)), capture_output=True,
                          text=True, timeout=300)
     assert bad.returncode != 0
+
+
+def test_bench_dump_outputs_cpu(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR`` writes the last timed step's loss / accuracy / parameters / gradient as
+    float32 ``.npy``; the same arguments give the same inputs, so two runs of the CPU path agree exactly.  A plain
+    run leaves the ``--full`` fields empty.  An array above the per-file cap becomes a fixed, seeded sample."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "INA_FAULT_STEP"):
+        env.pop(k, None)
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--device", "cpu", "--steps", "2",
+               "--warmup", "1", "--episodes-per-gpu", "2", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["phase_ms"] is None and out["params_in_sync"] is None
+        outs.append({n: np.load(tmp_path / d / n) for n in sorted(os.listdir(tmp_path / d))})
+    assert sorted(outs[0]) == ["accuracy.npy", "grad.npy", "loss.npy", "params.npy"]
+    for n, a in outs[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, outs[1][n]), n
+    assert abs(float(outs[0]["loss.npy"][0]) - out["final_loss"]) < 1e-5
+    assert outs[0]["params.npy"].shape == outs[0]["grad.npy"].shape and np.abs(outs[0]["grad.npy"]).max() > 0
+
+    sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 400)
+    x = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "s1"), {"x": x})
+    bench.dump_outputs(str(tmp_path / "s2"), {"x": x})
+    s = np.load(tmp_path / "s1" / "x.npy")
+    assert s.dtype == np.float64 and s.shape == (50,) and (np.diff(s) > 0).all()
+    assert np.array_equal(s, np.load(tmp_path / "s2" / "x.npy"))
